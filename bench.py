@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's benchmark contract for the CoDA hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload sa|model]
+    python bench.py --gpus N --steps K --warmup W [--workload sa|model] [--full] [--dump-outputs DIR]
 
 A "step" is one forward+backward pass of the hot path over one batch of 8
 synthetic SUN-RGBD-shaped scenes (20 000 points) per GPU, inputs resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0 (see the task contract):
 scenes/s over all ranks, plus
+
+A plain run measures the headline and nothing else: set-up, warm-up (with the settle blocks and the host-slack probe
+below), the K timed steps, the outputs of the last one if --dump-outputs is given, the line.  Everything else the
+line can carry is measured only with --full: the extra steps that time the other kernels (``roofline_others``, the
+whole-backward figures of ``roofline``), the unchanged caller's leg (``value_unchanged``), the ball query alone and at
+B = 64, the collectives timed alone (``comm``), the extra configurations and the CPU baseline.
 
 * ``roofline``     model workload: the dominant kernel of the step's critical path, the
                    encoder self-attention dK/dV kernel (fp32 MFMA bound): its flops per
@@ -33,6 +39,7 @@ import gc
 import json
 import math
 import os
+import re
 import sys
 import time
 
@@ -96,7 +103,18 @@ def parse():
                         "40k points / 512 queries / bf16 attention) that follow the headline measurement")
     p.add_argument("--prefetch", choices=["on", "off"], default="on",
                    help="model workload: sample (FPS) batch i+1 on a side stream during step i")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every secondary measurement (other kernels, the unchanged caller, "
+                        "collectives, extra configurations, CPU baseline); off: the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy (rank 0; the step starts from the "
+                        "state after the warm-up, so equal arguments give equal inputs)")
     return p.parse_args()
+
+
+# --dump-outputs: while this is a dict, every step function stores in it what its step computed (the loss, the loss
+# terms, the predictions); the timed loop runs with it set and the last step's entries are what gets written
+_capture = None
 
 
 def build_dry_workload(dev):
@@ -111,7 +129,10 @@ def build_dry_workload(dev):
     def step(model, batch, pre_encoded=None, with_dict=False):
         if dist.is_initialized():  # stands in for the SyncBatchNorm statistics exchange of the forward pass
             dist.all_reduce(torch.ones(32))
-        loss = model(batch["point_clouds"].reshape(-1, 3)).square().mean()
+        out = model(batch["point_clouds"].reshape(-1, 3))
+        loss = out.square().mean()
+        if _capture is not None:
+            _capture.update(loss=loss, outputs={"toy": out})
         return (loss, {"loss_toy": loss.detach(), "loss_toy_0": loss.detach() * 2}) if with_dict else loss
 
     return mod, step, "dry run of bench.py's control flow (toy CPU module, no kernels, numbers meaningless)", "dry"
@@ -131,8 +152,11 @@ def build_workload(kind, dev):
     mod.train()
 
     def step(model, batch):
-        _, feat, _ = model(batch["point_clouds"])
-        return feat.square().mean()
+        new_xyz, feat, inds = model(batch["point_clouds"])
+        loss = feat.square().mean()
+        if _capture is not None:
+            _capture.update(loss=loss, outputs={"new_xyz": new_xyz, "features": feat, "inds": inds})
+        return loss
 
     desc = ("configs[1]: PointNet++ SA (FPS 20000->2048 + ball_query r=0.2 nsample=64 + group + "
             "SharedMLP[3,64,128,256]+BN+ReLU + max-pool) fwd+bwd, batch=8/GPU, fp32")
@@ -281,6 +305,8 @@ def build_model_workload(dev, nq=256, config_tag="configs[2]", attn="fp32", imag
         with attention_core.mfma_dtype(attn) if dev.type == "cuda" else contextlib.nullcontext():
             pred = m(batch, curr_epoch=0, pre_encoded=pre_encoded) if pre_encoded is not None else m(batch, curr_epoch=0)
             loss, loss_dict = crit(pred, batch)
+        if _capture is not None:
+            _capture.update(loss=loss, loss_dict=loss_dict, outputs=pred["outputs"])
         return (loss, loss_dict) if with_dict else loss
 
     desc = (f"{config_tag}: full model_3detr (SA {'40000' if nq == 512 else '20000'}->2048 r=0.2 ns=64, enc 3L d=256 "
@@ -610,6 +636,77 @@ def make_batch_t(bsz, n, seed, dev):
     return torch.from_numpy(pc).to(dev)[..., :3].contiguous()
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 22  # elements kept of the flattened parameters / gradients (a fixed, seeded sample)
+
+
+def training_state(model, opt, dev):
+    """--dump-outputs: copies of all that a step reads and changes -- parameters and buffers, the optimizer's state,
+    the generators dropout draws its seeds from -- taken after the warm-up and put back before the timed region, so
+    that the timed steps start from the same state whatever number of settle steps ran in between."""
+    return {"model": {k: v.detach().clone() for k, v in model.state_dict().items()},
+            "opt": {p: {k: v.clone() if torch.is_tensor(v) else v for k, v in st.items()} for p, st in opt.state.items()},
+            "cpu_rng": torch.get_rng_state(),
+            "cuda_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None}
+
+
+def restore_training_state(model, opt, state, dev):
+    model.load_state_dict(state["model"])  # copies into the existing parameters: the optimizer keeps its references
+    for p in [p for p in opt.state if p not in state["opt"]]:
+        del opt.state[p]
+    for p, st in state["opt"].items():
+        cur = opt.state[p]
+        for k, v in st.items():
+            if torch.is_tensor(v) and torch.is_tensor(cur.get(k)) and cur[k].shape == v.shape:
+                cur[k].copy_(v)
+            else:
+                cur[k] = v.clone() if torch.is_tensor(v) else v
+    torch.set_rng_state(state["cpu_rng"])
+    if state["cuda_rng"] is not None:
+        torch.cuda.set_rng_state(state["cuda_rng"], dev)
+
+
+def _dump_array(t):
+    t = t.detach()
+    t = t.double() if not t.is_floating_point() or t.dtype == torch.float64 else t.float()
+    return t.cpu().numpy()
+
+
+def _fixed_sample(flat):
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat
+    idx = np.sort(np.random.default_rng(0).permutation(n)[:DUMP_SAMPLE])
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(path, captured, model):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it -- the loss, the loss
+    terms, the predictions of the last decoder layer (the set-abstraction features for --workload sa) and the updated
+    model: the parameters after the optimizer step and the (clipped) gradients it applied, both flattened in
+    ``named_parameters`` order and sampled at fixed positions.  float32 (float64 for integer results), one
+    DIR/<name>.npy per array."""
+    arrays = {"loss": captured["loss"]}
+    for k, v in (captured.get("loss_dict") or {}).items():
+        if torch.is_tensor(v):
+            arrays[k if k.startswith("loss") else "loss_" + k] = v
+    for k, v in (captured.get("outputs") or {}).items():
+        if torch.is_tensor(v):
+            arrays["out_" + k] = v
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays["param_sample"] = _fixed_sample(torch.cat([p.detach().reshape(-1) for p in params]))
+    arrays["grad_sample"] = _fixed_sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p))
+                                                     .detach().reshape(-1) for p in params]))
+    arrays = {re.sub(r"[^A-Za-z0-9_.-]", "_", k): _dump_array(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        sys.exit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": path, "files": len(arrays), "bytes": total}
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -648,6 +745,7 @@ def spawn_ranks(n):
 
 
 def main():
+    global _capture
     args = parse()
     dry = os.environ.get("CODA_BENCH_DRY") == "1"  # control-flow test on CPU, see build_dry_workload()
     if args.gpus < 1:
@@ -779,6 +877,7 @@ def main():
 
     for i in range(args.warmup):
         one_step(i)
+    state_after_warmup = training_state(raw_model, opt, dev) if args.dump_outputs else None
 
     # Settle: a fresh box can run the first seconds of a process with a host side ~1.4x slower than its steady state
     # (lazy loading of the libraries' code objects, page-ins: seen on 1 of 14 boxes in round 6 -- 413 instead of 557
@@ -820,8 +919,9 @@ def main():
     # first process host-bound -- 482 scenes/s with 16.2 ms of enqueue time per step measured on one box whose later
     # processes read 602.  Probe: five steps as they are against five steps with 1.5 ms of busy-waiting added to the host
     # side of each; a GPU-bound step hides the addition (difference ~0.1 ms), a host-bound one shows it in full.  While
-    # it shows (> 1.0 ms) the bench sleeps 5 s and probes again, at most 12 times; both figures go into the line
-    # (host.slack_probe_ms, host.wait_s).  Untimed, like the settle blocks; the timed region is unchanged.
+    # it shows (> 1.0 ms) the bench sleeps 5 s and probes again, at most 12 times (2 in a plain run, which stays within
+    # half a minute outside its steps); both figures go into the line (host.slack_probe_ms, host.wait_s).  Untimed,
+    # like the settle blocks; the timed region is unchanged.
     slack_probe_ms, host_wait_s = None, 0.0
     if not dry and kind == "model" and os.environ.get("CODA_BENCH_HOST_WAIT", "1") != "0":
         base_spin = spin["s"]
@@ -838,17 +938,23 @@ def main():
             settle_steps += 5
             return (time.perf_counter() - t_blk) / 5
 
-        for attempt in range(13):
+        attempts = 13 if args.full else 3
+        for attempt in range(attempts):
             diff = probe_block(1.5e-3) - probe_block(0.0)
             if world > 1:  # every rank must take the same decision
                 t = torch.tensor([diff], device=dev, dtype=torch.float64)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 diff = float(t.item())
             slack_probe_ms = diff * 1e3
-            if diff < 1.0e-3 or attempt == 12:
+            if diff < 1.0e-3 or attempt == attempts - 1:
                 break
             time.sleep(5.0)
             host_wait_s += 5.0
+
+    if state_after_warmup is not None:
+        sync()
+        restore_training_state(raw_model, opt, state_after_warmup, dev)
+        del state_after_warmup
 
     # the set-abstraction stage (and its side-stream sampling) is enqueued eagerly in both modes
     timing = _ext.enable_kernel_timing(["query_and_group_xyz", "ball_query", "furthest_point_sampling"])
@@ -885,6 +991,8 @@ def main():
     gc.callbacks.append(gc_probe)
     if world > 1:
         dist.barrier()
+    if args.dump_outputs:
+        _capture = {}  # every timed step refills it: the last one's results remain
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -897,6 +1005,8 @@ def main():
     dt = time.perf_counter() - t0
     gc.callbacks.remove(gc_probe)
     _ext.disable_kernel_timing()
+    captured, _capture = _capture, None
+    dumped = dump_outputs(args.dump_outputs, captured, raw_model) if captured is not None and rank == 0 else None
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -909,7 +1019,7 @@ def main():
     # Extra steps for the other attention kernels: single-process runs only.  A step contains the DDP
     # gradient all-reduce and the SyncBatchNorm exchange, so with several ranks every rank would have to run
     # them in lockstep; the multi-GPU lines report the dominant kernel (timed above) and the ball query only.
-    if attn_timed and world == 1:
+    if attn_timed and world == 1 and args.full:
         # every attention kernel (decoder shapes too), `steps` more EAGER steps outside the timed region.  When
         # the timed region replayed a hipGraph these also stand in for the dominant kernel: HIP events cannot
         # be read back from inside a graph replay (the rocprofv3 trace of the same command under profiles/
@@ -940,7 +1050,7 @@ def main():
     # lockstep, `steps` steps right after the headline's, same barrier + synchronize bracket, max over ranks.
     unchanged = None
     # CODA_BENCH_LEGS=headline: dev switch for kernel traces of the headline leg alone (tools/trace_gaps.py)
-    if kind in ("model", "dry") and os.environ.get("CODA_BENCH_LEGS", "both") != "headline":
+    if args.full and kind in ("model", "dry") and os.environ.get("CODA_BENCH_LEGS", "both") != "headline":
         model_u = model
         if reducer is not None:
             reducer.remove_hooks()
@@ -1013,23 +1123,24 @@ def main():
                                                  "all-reduce of the loss (engine.py:152) for the deferred finite check; "
                                                  "reduce_dict(loss_dict) (engine.py:153, logging only) is NOT in the "
                                                  "headline leg -- it is in value_unchanged"}
-        reps = 10
-        if reducer is not None:
-            names = ["early", "late"] if len(reducer.segments) == 2 else [str(k) for k in range(len(reducer.segments))]
-            comm["allreduce_ms"] = {n: round(timed_allreduce(seg.flat, reps), 4) for n, seg in zip(names, reducer.segments)}
-            comm["allreduce_bytes"] = {n: seg.flat.numel() * 4 for n, seg in zip(names, reducer.segments)}
-        else:
-            flat = torch.zeros(sum(p.numel() for p in raw_model.parameters() if p.requires_grad), device=dev)
-            comm["allreduce_ms"] = {"all": round(timed_allreduce(flat, reps), 4)}
-            comm["allreduce_bytes"] = {"all": flat.numel() * 4}
-        small = torch.zeros(512, dtype=torch.float64, device=dev)  # [sum, sum of squares] of a 256-channel layer
-        one = timed_allreduce(small, 50)
-        comm["syncbn_allreduce_ms_each"] = round(one, 4)
-        comm["syncbn_collectives_per_step"] = 16  # 8 BatchNorm layers x (forward statistics + backward sums)
-        comm["syncbn_ms"] = round(16 * one, 4)
+        if args.full:  # the collectives timed alone
+            reps = 10
+            if reducer is not None:
+                names = ["early", "late"] if len(reducer.segments) == 2 else [str(k) for k in range(len(reducer.segments))]
+                comm["allreduce_ms"] = {n: round(timed_allreduce(seg.flat, reps), 4) for n, seg in zip(names, reducer.segments)}
+                comm["allreduce_bytes"] = {n: seg.flat.numel() * 4 for n, seg in zip(names, reducer.segments)}
+            else:
+                flat = torch.zeros(sum(p.numel() for p in raw_model.parameters() if p.requires_grad), device=dev)
+                comm["allreduce_ms"] = {"all": round(timed_allreduce(flat, reps), 4)}
+                comm["allreduce_bytes"] = {"all": flat.numel() * 4}
+            small = torch.zeros(512, dtype=torch.float64, device=dev)  # [sum, sum of squares] of a 256-channel layer
+            one = timed_allreduce(small, 50)
+            comm["syncbn_allreduce_ms_each"] = round(one, 4)
+            comm["syncbn_collectives_per_step"] = 16  # 8 BatchNorm layers x (forward statistics + backward sums)
+            comm["syncbn_ms"] = round(16 * one, 4)
 
     alone = {}
-    if rank == 0 and prefetch:
+    if rank == 0 and prefetch and args.full:
         # with the sampling prefetch the operator ran on a side stream, competing with the step's own
         # kernels for CUs: also time it with the GPU to itself, `steps` launches on the same inputs
         alone = _ext.enable_kernel_timing(["query_and_group_xyz"])
@@ -1047,7 +1158,7 @@ def main():
     # time, below two launch latencies, so the bandwidth fraction at B = 8 measures launch-sized kernels; B = 64 is
     # the size at which the operator can be judged against the HBM roofline at all
     bq64 = None
-    if rank == 0 and world == 1 and kind == "model" and not dry and not args.no_extras:
+    if rank == 0 and world == 1 and kind == "model" and not dry and not args.no_extras and args.full:
         with torch.no_grad():
             big = torch.cat([make_batch_t(B_PER_GPU, N_POINTS, 777 + j, dev) for j in range(8)], 0)
             inds = _ext.furthest_point_sampling(big, M_CENTRES)
@@ -1166,31 +1277,34 @@ def main():
                                   "be read back): HIP events around each launch (coda_mha_timing_*, launch stream) in "
                                   "`steps` eagerly enqueued steps of the same workload right after it")
             # HBM bytes per launch from PMC (separate FETCH_SIZE / WRITE_SIZE passes), not collected in this run
-            via_ds = ("dqg", 2048, 2048) in attn_ms_all
-            roofline["traffic"] = ATTN_DKV_TRAFFIC_DS if via_ds else ATTN_DKV_TRAFFIC
-            roofline["traffic_source"] = ("profiles/r06_pmc_attention_hbm.md" if via_ds else "profiles/r03_pmc_attention_hbm.md") + \
-                " (PMC, separate FETCH_SIZE / WRITE_SIZE passes)"
-            if via_ds:
-                roofline["traffic_algorithmic"] = 5 * 16_777_216 + 536_870_912 + 2 * 16_777_216  # Q K V dO O in; dS dK dV out
+            # (which backward route ran -- through the dS workspace or not -- is seen in the extra steps of --full)
+            if attn_ms_all:
+                via_ds = ("dqg", 2048, 2048) in attn_ms_all
+                roofline["traffic"] = ATTN_DKV_TRAFFIC_DS if via_ds else ATTN_DKV_TRAFFIC
+                roofline["traffic_source"] = ("profiles/r06_pmc_attention_hbm.md" if via_ds else "profiles/r03_pmc_attention_hbm.md") + \
+                    " (PMC, separate FETCH_SIZE / WRITE_SIZE passes)"
+                if via_ds:
+                    roofline["traffic_algorithmic"] = 5 * 16_777_216 + 536_870_912 + 2 * 16_777_216  # Q K V dO O in; dS dK dV out
             # the part sustains 2.16 GHz under matrix load (tools/mfma_lds_probe.hip): what the nominal-clock peak becomes
             roofline["frac_of_sustained_clock_peak"] = round(roofline["achieved"] / (roofline["peak"] * 2.16 / 2.4), 4)
-            # (dK/dV from the timed region; delta and dQ from the extra steps when the timed region recorded dK/dV only)
-            bwd_kinds = ("delta", "dkv", "dq", "dqg", "ktp")
-            src = {k: (attn_ms if (k, 2048, 2048) in attn_ms else attn_ms_all) for k in bwd_kinds}
-            t_bwd = sum(sum(src[k][(k, 2048, 2048)]) / len(src[k][(k, 2048, 2048)])
-                        for k in bwd_kinds if (k, 2048, 2048) in src[k])
-            # the encoder layer's whole attention backward (delta + dK/dV + dQ launches): what it EXECUTES (dK/dV 8 + dQ
-            # GEMM 2 = 10 units of Lq * Lk * d through the dS workspace, 14 in the two-kernel form) and SURVEY 8d's
-            # algorithmic 8.  (Rounds 4-5 printed `frac_whole_backward_8d` with 12 units credited -- more than either.)
-            # priced like the single launches: the units on the three-piece bf16 path at 416.7, the others at 157.3
-            n_exec = 10 if via_ds else 14
-            n_x3 = (x3_units("dkv", 2048, 2048) + x3_units("dqg", 2048, 2048)) if via_ds else 0
-            peak_bwd = n_exec / ((n_exec - n_x3) / MFMA_F32_PEAK_TFLOPS + n_x3 / MFMA_X3_PEAK)
-            unit = 2048 * 2048 * 256 * B_PER_GPU / (t_bwd * 1e-3) / 1e12 / peak_bwd
-            roofline["frac_whole_backward_executed"] = round(n_exec * unit, 4)
-            roofline["frac_whole_backward_algorithmic"] = round(8 * unit, 4)
-            roofline["whole_backward_peak_tflops"] = round(peak_bwd, 1)
-            roofline["whole_backward_ms"] = round(t_bwd, 5)
+            if attn_ms_all:  # --full
+                # (dK/dV from the timed region; delta and dQ from the extra steps when the timed region recorded dK/dV only)
+                bwd_kinds = ("delta", "dkv", "dq", "dqg", "ktp")
+                src = {k: (attn_ms if (k, 2048, 2048) in attn_ms else attn_ms_all) for k in bwd_kinds}
+                t_bwd = sum(sum(src[k][(k, 2048, 2048)]) / len(src[k][(k, 2048, 2048)])
+                            for k in bwd_kinds if (k, 2048, 2048) in src[k])
+                # the encoder layer's whole attention backward (delta + dK/dV + dQ launches): what it EXECUTES (dK/dV 8 + dQ
+                # GEMM 2 = 10 units of Lq * Lk * d through the dS workspace, 14 in the two-kernel form) and SURVEY 8d's
+                # algorithmic 8.  (Rounds 4-5 printed `frac_whole_backward_8d` with 12 units credited -- more than either.)
+                # priced like the single launches: the units on the three-piece bf16 path at 416.7, the others at 157.3
+                n_exec = 10 if via_ds else 14
+                n_x3 = (x3_units("dkv", 2048, 2048) + x3_units("dqg", 2048, 2048)) if via_ds else 0
+                peak_bwd = n_exec / ((n_exec - n_x3) / MFMA_F32_PEAK_TFLOPS + n_x3 / MFMA_X3_PEAK)
+                unit = 2048 * 2048 * 256 * B_PER_GPU / (t_bwd * 1e-3) / 1e12 / peak_bwd
+                roofline["frac_whole_backward_executed"] = round(n_exec * unit, 4)
+                roofline["frac_whole_backward_algorithmic"] = round(8 * unit, 4)
+                roofline["whole_backward_peak_tflops"] = round(peak_bwd, 1)
+                roofline["whole_backward_ms"] = round(t_bwd, 5)
             note = "HIP events around each launch, `steps` extra steps right after the timed region"
             for key in sorted(attn_ms_all, key=lambda k: (-k[1] * k[2], k[0])):
                 if key[0] not in ("delta", "dqr", "ktp") and key != dom:
@@ -1349,7 +1463,7 @@ def main():
             # sees the figures the north-star bars are read on)
             lead = [o for o in others if o["kernel"].startswith(("decoder_aggregate", "sa_mlp_aggregate", "grid_build_kernel"))]
             out["roofline_others"] = lead + [o for o in others if o not in lead]
-        if world == 1 and not dry and not args.no_extras and kind == "model" and args.workload != "model40k":
+        if world == 1 and not dry and not args.no_extras and kind == "model" and args.workload != "model40k" and args.full:
             # extra keys, measured by this same command right after the headline (fewer steps: they are
             # secondary lines; the headline's timed region above is untouched by them)
             ex_steps, ex_warm = max(5, min(args.steps, 10)), 3
@@ -1360,7 +1474,7 @@ def main():
                                     "clip_image_tower": run_image_tower(dev, ex_steps, ex_warm),
                                     "alignment_loss_stage2_classes": run_alignment_extra(dev),
                                     "configs[2]_with_image_branch": run_extra("distill", dev, ex_steps, ex_warm)}
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if world == 1 and not args.no_cpu_baseline and not dry and args.full:
             out["cpu_baseline"] = cpu_baseline(kind)
         if (world == 1 and not dry and unchanged is not None and ("extra_configs" in out or "cpu_baseline" in out)
                 and os.environ.get("CODA_BENCH_UNCHANGED_REPEAT", "1") != "0"):
@@ -1380,6 +1494,8 @@ def main():
                 unchanged["ms_per_step"] = round(dt3 / args.steps * 1e3, 4)
             out["config"]["value_unchanged"] = out["value_unchanged"] = unchanged["value"]
             out["ms_per_step_unchanged"] = unchanged["ms_per_step"]
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if dry:
             out.update(metric="dry run (control flow only)", data="none", dtype="f32")
         line = compact_line(out, dry)

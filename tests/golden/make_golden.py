@@ -26,6 +26,7 @@ REF = "/root/reference"
 sys.path.insert(0, ROOT)
 
 from oracle import pointnet2_oracle as O  # noqa: E402
+from tests.golden import parts  # noqa: E402
 from coda_neurips2023_amd.synthetic_scenes import make_batch  # noqa: E402
 
 
@@ -97,9 +98,8 @@ FMA_MODE = O.DEFAULT_FMA_MODE  # distance-arithmetic mode of the oracle ops whil
 
 def _save(name, **arrays):
     arrays["fma_mode"] = np.int32(O.get_fma_mode())
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+    for path in parts.save(name, arrays, HERE):  # (split into parts when above a committed file's size)
+        print(f"wrote {path}  ({os.path.getsize(path) / 1024:.1f} KiB)")
 
 
 # --------------------------------------------------------------------------------------

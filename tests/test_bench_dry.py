@@ -39,7 +39,7 @@ def _check(out, world, steps, warmup):
 
 
 def test_single_process_flow():
-    out = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1"])
+    out = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full"])
     _check(out, 1, 3, 1)
     assert "cpu_baseline" not in out  # the dry run measures nothing, least of all the oracle
     # the unchanged caller's leg (engine.py:136-164 with its blocking finite check) is reported at top level
@@ -52,7 +52,7 @@ def test_single_process_flow():
 def test_plain_command_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (the driver's scaling command may be exactly that):
     bench.py starts the two ranks itself, like the reference's main.py:1103-1108."""
-    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"])
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"])
     _check(out, 2, 3, 1)
     _check_multi(out, 2)
     assert "bench.py itself" in out["comm"]["launched_by"]
@@ -88,7 +88,7 @@ def test_a_failing_rank_takes_the_job_down():
 def test_two_ranks_run_the_same_collectives():
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", "29541", "bench.py", "--gpus", "2", "--steps", "3",
-                "--warmup", "1"])
+                "--warmup", "1", "--full"])
     _check(out, 2, 3, 1)
     _check_multi(out, 2)
 
@@ -108,6 +108,48 @@ def test_eight_ranks_like_the_scaling_run():
     """the driver's 8-GPU command line, on 8 CPU processes"""
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                 "--master-addr", "127.0.0.1", "--master-port", "29547", "bench.py", "--gpus", "8", "--steps", "2",
-                "--warmup", "1"])
+                "--warmup", "1", "--full"])
     _check(out, 8, 2, 1)
     _check_multi(out, 8)
+
+
+def test_plain_run_is_the_headline_alone():
+    """without --full the line carries the headline and none of the secondary legs; --steps is the timed step count"""
+    out = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "2"])
+    _check(out, 1, 4, 2)
+    for k in ("value_unchanged", "ms_per_step_unchanged", "extra_configs", "cpu_baseline", "roofline_others"):
+        assert k not in out, k
+    assert out["comm"]["rccl_ranks"] == 1
+
+
+@pytest.mark.timeout(300)
+def test_plain_two_ranks_skip_the_collective_timings():
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1"])
+    _check(out, 2, 2, 1)
+    assert out["comm"]["rccl_ranks"] == 2 and "allreduce_ms" not in out["comm"]
+    assert "value_unchanged" not in out
+
+
+def test_dump_outputs_are_repeatable(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files of the last timed step, at most 64 MB, equal for equal arguments
+    (the timed steps start from the state after the warm-up)"""
+    import numpy as np
+    runs = []
+    for r in range(2):
+        d = tmp_path / f"run{r}"
+        out = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)])
+        _check(out, 1, 3, 2)
+        files = sorted(p.name for p in d.iterdir())
+        assert out["dump_outputs"]["files"] == len(files)
+        assert {"loss.npy", "param_sample.npy", "grad_sample.npy", "out_toy.npy"} <= set(files)
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys()
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+    # a different number of timed steps: the last step sees other parameters
+    d = tmp_path / "steps4"
+    _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "2", "--dump-outputs", str(d)])
+    assert not np.array_equal(np.load(d / "param_sample.npy"), runs[0]["param_sample.npy"])

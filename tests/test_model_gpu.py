@@ -9,6 +9,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+from golden import parts as golden_parts  # noqa: E402
 from golden.weights import fill_deterministic, grad_digest  # noqa: E402
 from test_model_structure import tiny_args  # noqa: E402
 
@@ -23,7 +24,7 @@ def _golden_distance_mode(_distance_mode_default):
     """FPS / ball_query inside the model run in the mode the fixture was generated in."""
     from tests._modes import fixture_mode, set_distance_mode
     set_distance_mode(fixture_mode(G))
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "model_tiny.npz"))
+G = golden_parts.load("model_tiny.npz")
 RTOL = 1e-3
 
 

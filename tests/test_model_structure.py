@@ -9,8 +9,9 @@ import torch
 from coda_neurips2023_amd import box_util
 from coda_neurips2023_amd.dataset_config import HotPathDatasetConfig
 from coda_neurips2023_amd.model_3detr import build_model, default_args
+from tests.golden import parts as golden_parts
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "model_tiny.npz"))
+G = golden_parts.load("model_tiny.npz")
 
 
 def tiny_args():

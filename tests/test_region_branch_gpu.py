@@ -13,12 +13,13 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(__file__))
+from golden import parts as golden_parts  # noqa: E402
 from golden import region_inputs as R  # noqa: E402
 
 from coda_neurips2023_amd import box_util, clip_crops, clip_labels  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "region_branch.npz"))
+G = golden_parts.load("region_branch.npz")
 
 
 def _provider(flags, tower, method):

@@ -6,7 +6,7 @@ VAR=$1; REPS=$2; STEPS=$3; shift 3
 for r in $(seq $REPS); do
   for v in "$@"; do
     if [ "$v" = "-" ]; then E="env -u $VAR"; else E="env $VAR=$v"; fi
-    $E python bench.py --no-cpu-baseline --no-extras --steps $STEPS --warmup 10 2>/dev/null | python -c "
+    $E python bench.py --full --no-cpu-baseline --no-extras --steps $STEPS --warmup 10 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$VAR=$v', d['value'], d['ms_per_step'], d.get('config', {}).get('value_unchanged'), d['roofline'].get('avg_launch_ms'))"

@@ -1,7 +1,8 @@
 #!/bin/bash
-# dev: copies what tools/run_round_end.sh left under gpurun_out/final_* into profiles/<tag>_* (run here, after the gpurun call)
+# dev: copies what tools/run_round_end.sh left under $OUT/final_* into profiles/<tag>_*, once $OUT is back from the GPU box.
+# Usage: OUT=<dir> bash tools/collect_round_end.sh [tag]
 cd "$(dirname "$0")/.." || exit 1
-T=${1:-r06}; G=gpurun_out; P=profiles
+T=${1:-r06}; G=${OUT:?set OUT to the directory tools/run_round_end.sh wrote}; P=profiles
 cp $G/final_bench.json $P/${T}_bench_line.json
 cp $G/final_bench_with_extras_full.json $P/${T}_bench_with_extras.json
 { tail -3 $G/final_tests.log; tail -1 $G/final_smoke.log; } > $P/${T}_gpu_tests_tail.txt

@@ -7,5 +7,5 @@ import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', d['value'], d['ms_per_step'], 'unchanged', d.get('value_unchanged'), d['host'])"; }
 CODA_BENCH_SETTLE_S=${FIRST_SETTLE_S:-6} python bench.py 2>/dev/null | show "first (default invocation)"
-python bench.py --no-cpu-baseline --no-extras 2>/dev/null | show "second"
-python bench.py --no-cpu-baseline --no-extras 2>/dev/null | show "third"
+python bench.py --full --no-cpu-baseline --no-extras 2>/dev/null | show "second"
+python bench.py --full --no-cpu-baseline --no-extras 2>/dev/null | show "third"
